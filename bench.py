@@ -18,7 +18,15 @@ are visible.  Total work is fixed as N grows ("scaling": "strong"); `value` =
 distinct states of the check / seconds per check.  --logical-shards W runs the
 same sharded protocol with W shards on one GPU (the protocol's overhead).
 
+A plain run does only what the headline needs: set up, W warm-up checks, K
+timed checks, the result line.  --full adds what takes a run of its own: the
+CPU baseline (`cpu_baseline`, a bounded run of the CPU engine on the same cfg).
+--dump-outputs DIR writes what the last timed check returned to its caller as
+DIR/counts.npy and DIR/levels.npy (float64); the model constants are the only
+input, so two builds given the same arguments can be compared file for file.
+
 Run:  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+                      [--full] [--dump-outputs DIR]
 """
 import argparse
 import glob
@@ -136,13 +144,34 @@ def cpu_baseline(module, cfg_path, seconds=15.0):
     return out
 
 
+DUMP_COUNTS = ("generated", "distinct", "left", "depth", "status", "hidden_var_collisions")
+
+
+def dump_outputs(path, res):
+    """--dump-outputs: what the check returned to its caller, without the times
+    and capacities that vary from run to run.  counts.npy = DUMP_COUNTS in that
+    order (status as rmc.h's code), levels.npy = rmc_levels' two counts per BFS
+    level; float64 holds every count exactly (all far below 2^53)."""
+    import numpy as np
+    import raftmc
+    code = {v: k for k, v in raftmc.STATUS.items()}
+    os.makedirs(path, exist_ok=True)
+    counts = [code.get(res[k], -1) if k == "status" else res[k] for k in DUMP_COUNTS]
+    np.save(os.path.join(path, "counts.npy"), np.array(counts, dtype=np.float64))
+    np.save(os.path.join(path, "levels.npy"), np.array(res["levels"], dtype=np.float64).reshape(-1, 2))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default=os.environ.get("RMC_WORKLOAD", DEFAULT_WORKLOAD))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes a run of its own: the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed check's results as DIR/counts.npy and DIR/levels.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--logical-shards", type=int, default=0)
     ap.add_argument("--chunk", type=int, default=0, help="parents per k_expand launch (0 = librmc's default)")
@@ -158,6 +187,9 @@ def main():
         sys.exit(2)
     if args.gpus < 1:
         print("bench.py: --gpus must be at least 1", file=sys.stderr)
+        sys.exit(2)
+    if args.steps < 1 or args.warmup < 0:
+        print("bench.py: --steps must be at least 1 and --warmup at least 0", file=sys.stderr)
         sys.exit(2)
     inproc = world == 1 and args.gpus > 1  # the library's n_gpus front door, one host thread per GPU
     dist = None
@@ -313,7 +345,9 @@ def main():
             xb = (G * 17 + D * (S + 10)) * (nw - 1) / nw
             line["xgmi"] = {"bytes": xb, "per_gpu_GBps": xb / nw / per_step / 1e9,
                             "peak_per_gpu_GBps": 7 * 153.0}
-        if world == 1 and not inproc and not args.no_cpu_baseline:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, res)
+        if args.full and world == 1 and not inproc and not args.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = cpu_baseline(module, cfg_rel, args.cpu_seconds)
             except Exception as e:  # report, never hide

@@ -12,7 +12,7 @@ if [ "${TESTS:-all}" != "none" ]; then
   [ $rc -eq 0 ] || exit $rc
 fi
 if [ "${BENCH:-1}" = 1 ]; then
-  cpu="--no-cpu-baseline"; [ "${CPU:-0}" = 1 ] && cpu=""
+  cpu=""; [ "${CPU:-0}" = 1 ] && cpu="--full"
   timeout -k 10 ${BENCH_LIMIT:-400} python -u bench.py $cpu $BENCH_ARGS > gpurun_out/bench_$TAG.json 2> gpurun_out/bench_$TAG.err; rc=$?
   echo "bench rc=$rc"; cat gpurun_out/bench_$TAG.json; tail -3 gpurun_out/bench_$TAG.err
   [ $rc -eq 0 ] || exit $rc

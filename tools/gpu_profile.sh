@@ -11,7 +11,7 @@ CFG=${CFG:-Raft_n3v2e2}
 O=$R/gpurun_out/prof_$TAG
 mkdir -p $O
 set -o pipefail
-timeout -k 10 420 python -u bench.py --workload $WL $BENCH_ARGS > $O/bench.json 2> $O/bench.err || { echo "bench failed"; exit 1; }
+timeout -k 10 420 python -u bench.py --full --workload $WL $BENCH_ARGS > $O/bench.json 2> $O/bench.err || { echo "bench failed"; exit 1; }
 cat $O/bench.json
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/kt -o run --output-format csv -- python3 $R/bench.py --workload $WL --no-cpu-baseline --steps 2 --warmup 1 > $O/kt.log 2>&1 || { echo "kernel-trace failed"; exit 1; }
