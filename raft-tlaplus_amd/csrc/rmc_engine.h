@@ -127,7 +127,8 @@ void read_fpstats(unsigned long long* out);
 bool diag_build();  // compiled with -DRMC_DIAG (k_expand phase cutoffs)  // -DRMC_FPSTATS diagnostic builds (8 counters, rmc_fpset.h)
 void launch_simulate(int spec, int N, const uint32_t* init, unsigned long long walkers, unsigned depth,
                      unsigned long long seed, uint16_t* binds, unsigned long long* counters, SimStatus* ss,
-                     DevStatus* st, int words, hipStream_t s);
+                     DevStatus* st, int words, hipStream_t s, uint32_t* steps_out = nullptr,
+                     uint32_t* rows_out = nullptr);  // test hook outputs: per-walker steps, final rows
 
 // host-side (rmc_host.cpp): replay + formatting use the same action code
 int host_eval_apply(const Model& M, const uint32_t* parent, int binding, uint32_t* out, int* ordinal, int* act,

@@ -2399,6 +2399,9 @@ void launch_multi_copy(const CopyDesc* d, int n, unsigned long long max_bytes, h
 // uniformly at random, writes it, and checks the cfg's invariants on it.  A
 // state with no successor ends the behaviour (-deadlock).  The chosen bindings
 // are recorded so the host can replay a violating behaviour into a trace.
+// steps_out / rows_out (both null in rmc_simulate; the test hook
+// rmc_selftest_simulate_round passes them): every walker's step count and its
+// final packed row.
 __device__ __forceinline__ unsigned long long splitmix(unsigned long long& x) {
   unsigned long long z = (x += 0x9E3779B97F4A7C15ULL);
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
@@ -2410,7 +2413,8 @@ template <int SPEC, int N>
 __global__ __launch_bounds__(SIM_BLOCK) void k_simulate(const uint32_t* __restrict__ init, unsigned long long walkers,
                                                         unsigned depth, unsigned long long seed, uint16_t* __restrict__ binds,
                                                         unsigned long long* __restrict__ counters, SimStatus* ss,
-                                                        DevStatus* st) {
+                                                        DevStatus* st, uint32_t* __restrict__ steps_out,
+                                                        uint32_t* __restrict__ rows_out) {
   extern __shared__ __align__(16) unsigned char lds[];
   const int words = cM.words, Wp = words | 1;
   const int tid = threadIdx.x;
@@ -2459,20 +2463,26 @@ __global__ __launch_bounds__(SIM_BLOCK) void k_simulate(const uint32_t* __restri
   }
   atomicAdd(&counters[0], (unsigned long long)steps);  // states generated by this behaviour (after Init)
   atomicMax(&counters[1], (unsigned long long)steps);
+  if (steps_out) {  // test hook only (uniform: a kernel argument)
+    steps_out[w] = steps;
+    if (rows_out)
+      for (int q = 0; q < words; q++) rows_out[w * (unsigned long long)words + q] = cur[q];
+  }
 }
 template <int SPEC, int N>
 static void launch_sim_t(const uint32_t* init, unsigned long long walkers, unsigned depth, unsigned long long seed,
                          uint16_t* binds, unsigned long long* counters, SimStatus* ss, DevStatus* st, int words,
-                         hipStream_t s) {
+                         hipStream_t s, uint32_t* steps_out, uint32_t* rows_out) {
   size_t lds = (size_t)SIM_BLOCK * ((words | 1) + words) * 4;
   hipLaunchKernelGGL((k_simulate<SPEC, N>), dim3((unsigned)((walkers + SIM_BLOCK - 1) / SIM_BLOCK)), dim3(SIM_BLOCK),
-                     lds, s, init, walkers, depth, seed, binds, counters, ss, st);
+                     lds, s, init, walkers, depth, seed, binds, counters, ss, st, steps_out, rows_out);
 }
 void launch_simulate(int spec, int N, const uint32_t* init, unsigned long long walkers, unsigned depth,
                      unsigned long long seed, uint16_t* binds, unsigned long long* counters, SimStatus* ss,
-                     DevStatus* st, int words, hipStream_t s) {
-#define RMC_SIM(SP, NN) \
-  if (spec == SP && N == NN) return launch_sim_t<SP, NN>(init, walkers, depth, seed, binds, counters, ss, st, words, s);
+                     DevStatus* st, int words, hipStream_t s, uint32_t* steps_out, uint32_t* rows_out) {
+#define RMC_SIM(SP, NN)      \
+  if (spec == SP && N == NN) \
+    return launch_sim_t<SP, NN>(init, walkers, depth, seed, binds, counters, ss, st, words, s, steps_out, rows_out);
   RMC_SIM(RAFT, 3)
 #ifndef RMC_DEV_ONE
   RMC_SIM(RAFT, 2) RMC_SIM(RAFT, 4) RMC_SIM(RAFT, 5)

@@ -146,6 +146,10 @@ def lib():
     L.rmc_trace_module.argtypes = [P, ctypes.c_char_p, ctypes.c_char_p, c_size_t, ctypes.c_char_p, c_size_t]
     L.rmc_trace_json.argtypes = [P, ctypes.c_char_p, c_size_t]
     L.rmc_selftest_random_trace.argtypes = [P, ctypes.c_uint64, c_int]
+    L.rmc_selftest_simulate_words.argtypes = [P, ctypes.POINTER(Options)]
+    L.rmc_selftest_simulate_round.argtypes = [P, ctypes.POINTER(Options), ctypes.c_uint64, ctypes.c_uint32,
+                                              ctypes.c_uint64, ctypes.c_uint64, P, P, P, P]
+    L.rmc_selftest_replay_binds.argtypes = [P, P, c_int]
     L.rmc_selftest_set_hint_kmax.argtypes = [P, ctypes.c_uint32]
     L.rmc_selftest_widenings.argtypes = [P, ctypes.POINTER(ctypes.c_uint64), c_int]
     L.rmc_selftest_profile_expand.argtypes = [P, ctypes.POINTER(Options), c_int, ctypes.POINTER(ctypes.c_double), c_int]
@@ -373,6 +377,47 @@ class Model:
     def selftest_random_trace(self, seed, steps):
         """TEST HOOK: a seeded host random walk replayed into the model's trace (not a product path)."""
         n = lib().rmc_selftest_random_trace(self._h, seed, steps)
+        if n < 0:
+            raise RaftmcError(lib().rmc_last_error().decode())
+        return n
+
+    def selftest_simulate_round(self, walkers, depth, seed=0, round=0, rows=True, host_replay=True, **kw):
+        """TEST HOOK: round `round` of simulate(walkers=, depth=, seed=) as one launch,
+        with what every walker did (numpy arrays): binds uint16[walkers, depth]
+        (row w's first steps[w] entries are its behaviour; the rest read 0xFFFF
+        or a binding that was not applied), steps uint32[walkers], rows
+        uint32[walkers, words] (final packed rows; None if rows=False), status
+        (as simulate reports the round) and, with host_replay, mismatch: the host
+        replay's {kind: (count, first walker)} for binding_not_enabled,
+        final_row, stopped_early and invariant (all counts 0 = device == host)."""
+        import numpy as np
+        L = lib()
+        o = self._options(**kw)
+        words = L.rmc_selftest_simulate_words(self._h, ctypes.byref(o))
+        if words < 0:
+            raise RaftmcError(L.rmc_last_error().decode())
+        walkers, depth = int(walkers), int(depth)
+        binds = np.empty((walkers, depth), dtype=np.uint16)
+        steps = np.empty(walkers, dtype=np.uint32)
+        rowbuf = np.empty((walkers, words), dtype=np.uint32) if rows else None
+        mm = np.zeros(8, dtype=np.uint64) if host_replay else None
+        rc = L.rmc_selftest_simulate_round(self._h, ctypes.byref(o), walkers, depth, int(seed) & (2**64 - 1), int(round),
+                                           binds.ctypes.data, steps.ctypes.data,
+                                           rowbuf.ctypes.data if rows else None,
+                                           mm.ctypes.data if host_replay else None)
+        if rc < 0:
+            raise RaftmcError(L.rmc_last_error().decode())
+        out = dict(binds=binds, steps=steps, rows=rowbuf, status=STATUS.get(rc, str(rc)))
+        if host_replay:
+            kinds = ["binding_not_enabled", "final_row", "stopped_early", "invariant"]
+            out["mismatch"] = {k: (int(mm[2 * i]), int(mm[2 * i + 1])) for i, k in enumerate(kinds)}
+        return out
+
+    def selftest_replay_binds(self, binds):
+        """TEST HOOK: load a binding chain into the model's trace (as after a violation);
+        returns the number of states.  A binding that is not enabled raises."""
+        arr = (ctypes.c_uint16 * max(len(binds), 1))(*[int(b) for b in binds])
+        n = lib().rmc_selftest_replay_binds(self._h, arr, len(binds))
         if n < 0:
             raise RaftmcError(lib().rmc_last_error().decode())
         return n

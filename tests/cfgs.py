@@ -442,10 +442,10 @@ _REJAE_REF = _REJAE % """\\/ m.mterm < currentTerm[i]
               \\/ /\\ m.mterm = currentTerm[i]
                  /\\ state[i] = Follower
                  /\\ \\lnot logOk"""
-_REJAE_LENIDX = (_REJAE % """\/ m.mterm < currentTerm[i]
-              \/ /\ m.mterm = currentTerm[i]
-                 /\ state[i] = Follower
-                 /\ \lnot logOk""").replace("mmatchIndex     |-> 0", "mmatchIndex     |-> Len(log[i])")
+_REJAE_LENIDX = (_REJAE % """\\/ m.mterm < currentTerm[i]
+              \\/ /\\ m.mterm = currentTerm[i]
+                 /\\ state[i] = Follower
+                 /\\ \\lnot logOk""").replace("mmatchIndex     |-> 0", "mmatchIndex     |-> Len(log[i])")
 _UPDATETERM_STAY = """/\\ m.mterm > currentTerm[m.mdest]
     /\\ currentTerm'    = [currentTerm EXCEPT ![m.mdest] = m.mterm]
     /\\ votedFor'       = [votedFor    EXCEPT ![m.mdest] = Nil]

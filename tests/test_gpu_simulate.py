@@ -1,6 +1,8 @@
 """GPU: random simulation (TLC -simulate) through the C ABI.
 
-Simulation is random, so there are no oracle counts to match; what is pinned:
+Every walker of a round against the host replay and the oracle (each step a
+Next step, the draw's exact law, the counters summed over the rounds, the step
+cap) is pinned in test_gpu_simulate_oracle.py; what is pinned here, on whole runs:
 known-unsafe configs yield the oracle's violated invariant with a behaviour
 that the independent Python oracle replays from its own Init through its own
 Next (every step must be one of the oracle's successors, as TLC would check a
