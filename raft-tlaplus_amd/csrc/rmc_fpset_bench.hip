@@ -65,6 +65,23 @@ __global__ __launch_bounds__(256) void k_batch(unsigned long long* T, unsigned l
   }
 }
 
+// After the timed batch (untimed): what the table and the batch's returned
+// slots really hold -- cnt[0] += entries of E[0..n) whose key is not EMPTY
+// (stride 2 words: the table), cnt[1] += words of R[0..nr) equal to EMPTY (the
+// inserts that found no slot).  Checked against present + new by the test.
+__global__ __launch_bounds__(256) void k_audit(const unsigned long long* E, unsigned long long n,
+                                               const unsigned long long* R, unsigned long long nr,
+                                               unsigned long long* cnt) {
+  const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
+  unsigned long long occ = 0, fail = 0;
+  for (unsigned long long j = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += stride)
+    occ += E[2 * j] != EMPTY;
+  for (unsigned long long j = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; j < nr; j += stride)
+    fail += R[j] == EMPTY;
+  if (occ) atomicAdd(cnt, occ);
+  if (fail) atomicAdd(cnt + 1, fail);
+}
+
 // Counter calibration (MI355X_MICROARCH.md: FETCH_SIZE / WRITE_SIZE are
 // calibrated only for wide streaming accesses): n random 16 B reads (one
 // entry, one 128 B line each) of a table far larger than the 256 MiB
@@ -118,11 +135,12 @@ int main(int argc, char** argv) {
     return 2;
   }
   const unsigned long long slots = 1ULL << slots_log2, mask = slots - 1;
-  unsigned long long *T = nullptr, *slot = nullptr, *ctr = nullptr;
+  unsigned long long *T = nullptr, *slot = nullptr, *ctr = nullptr, *audit = nullptr;
   rmc::DevStatus* st = nullptr;
   CK(hipMalloc(&T, slots * 16));
   CK(hipMalloc(&slot, batch * 8));
   CK(hipMalloc(&ctr, 8));
+  CK(hipMalloc(&audit, 16));
   CK(hipMalloc(&st, sizeof(rmc::DevStatus)));
   hipEvent_t e0, e1;
   CK(hipEventCreate(&e0));
@@ -172,18 +190,26 @@ int main(int argc, char** argv) {
     rmc::DevStatus hs;
     CK(hipMemcpy(&added, ctr, 8, hipMemcpyDeviceToHost));
     CK(hipMemcpy(&hs, st, sizeof hs, hipMemcpyDeviceToHost));
+    // outside the event pair: the table's occupied entries and the batch's failed inserts
+    unsigned long long aud[2] = {0, 0};
+    CK(hipMemset(audit, 0, 16));
+    hipLaunchKernelGGL(rmc::k_audit, dim3(grid), dim3(256), 0, 0, T, slots, slot, batch, audit);
+    CK(hipGetLastError());
+    CK(hipMemcpy(aud, audit, 16, hipMemcpyDeviceToHost));
     const double s = ms * 1e-3;
     // line-granular traffic: every insert reads one 128 B line; a new key
     // also writes it back (duplicates of earlier levels leave it clean)
     printf("{\"slots_log2\": %d, \"load\": %.3f, \"batch\": %llu, \"dup\": %.3f, \"new\": %llu, \"ms\": %.3f, "
-           "\"inserts_per_s\": %.4g, \"line_GBps_min\": %.1f, \"table_full\": %d}\n",
+           "\"inserts_per_s\": %.4g, \"line_GBps_min\": %.1f, \"table_full\": %d, \"present\": %llu, "
+           "\"occupied\": %llu, \"failed\": %llu}\n",
            slots_log2, (double)(present + added) / (double)slots, batch, dup, added, ms, batch / s,
-           (batch * 128.0 + added * 128.0) / s / 1e9, hs.cap_flags != 0);
+           (batch * 128.0 + added * 128.0) / s / 1e9, hs.cap_flags != 0, present, aud[0], aud[1]);
     fflush(stdout);
   }
   CK(hipFree(T));
   CK(hipFree(slot));
   CK(hipFree(ctr));
+  CK(hipFree(audit));
   CK(hipFree(st));
   return 0;
 }

@@ -24,3 +24,7 @@ def test_fpset_bench_small():
         assert r["table_full"] == 0
         assert abs(r["new"] / r["batch"] - (1 - r["dup"])) < 0.02  # duplicate ratio as asked
         assert r["inserts_per_s"] > 0
+        # the table itself, counted after the timed batch: every prefilled key and
+        # every new key of the batch is stored once, and no insert came back empty
+        assert r["occupied"] == r["present"] + r["new"]
+        assert r["failed"] == 0
